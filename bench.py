@@ -83,6 +83,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary lines (forward only, bf16 decoders, trained-like tables)")
     ap.add_argument("--side", default="", choices=["", "dp_rank_local"],
                     help="(internal) run ONE side measurement and print its JSON: what side_process() starts as a child of the N = 1 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32, rank 0, at most 64 MB): "
+                         "its loss, its per-ray outputs (MapStep.rendered()) and the decoders' and tables' parameters its Adam step left.  "
+                         "Same arguments, same inputs; two runs agree to rounding for a few steps, then the fp32 atomics of the table "
+                         "gradient, amplified by Adam, move them apart: compare builds at a small --warmup + --steps")
     return ap.parse_args(argv)
 
 
@@ -297,6 +302,32 @@ def encoder_request_roofline(descs, pts, kernel_ms):
             "curve": "profiles/r06_ta_bench.txt (tools/ta_bench.hip; tools/gather_scope.hip: the same rate with loads that bypass the CU's cache)",
             "note": "ceiling = sum over levels and grids of lane loads / rate(slab bytes); uniformly random addresses in the microbenchmark, so "
                     "levels whose samples share lines run ahead of it"}
+
+
+DUMP_BYTES = 64 * 2 ** 20                                        # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """
+    Write {name: float array} as out_dir/<name>.npy (float32).  Over the budget, every array of more than 4096 elements is replaced by a
+    fixed, seeded sample of its flattened elements (sorted indices: the same from run to run and build to build).
+    Returns {name: [shape written, shape computed]}.
+    """
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.size <= 4096)
+    big = sum(a.nbytes for a in arrays.values() if a.size > 4096)
+    frac = 1.0 if small + big <= budget else (budget - small) / big
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k, a in arrays.items():
+        full = list(a.shape)
+        if frac < 1.0 and a.size > 4096:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        shapes[k] = [list(a.shape), full]
+    return shapes
 
 
 def _median(xs):
@@ -976,11 +1007,18 @@ def run_rank(args):
     #  is itself reduced over the ranks -- a wall-clock test per rank let them part ways and wait for each other forever)
     from unislam_amd.dist import all_agree as _all_agree
     all_agree = lambda flag: _all_agree(flag, True if world > 1 else None, dev)
+    # the set-up runs as many iterations as fit in its wall time: the state they reached is put back afterwards, so that the W + K steps
+    # start from the same model, optimiser state and random streams in every run (what --dump-outputs writes depends on nothing else)
+    keep = (step.flat.clone(), step.m.clone(), step.v.clone(), step.step_dev.clone(), step.opt_step, step.rng_calls)
     t_pre = time.perf_counter()
     while all_agree(time.perf_counter() - t_pre < args.prewarm_s):
         for _ in range(20):
             nxt()
         torch.cuda.synchronize()
+    step.flat.copy_(keep[0]); step.m.copy_(keep[1]); step.v.copy_(keep[2]); step.step_dev.copy_(keep[3])
+    step.opt_step, step.rng_calls = keep[4], keep[5]
+    del keep
+    barrier()
     for _ in range(args.warmup):
         loss = nxt()
     barrier()
@@ -994,6 +1032,16 @@ def run_rank(args):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     el = float(t.item())
     ms = 1e3 * el / args.steps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the K-th timed step computed, before anything else runs on this model: its loss and per-ray outputs, and the decoders and
+        # tables as its Adam step left them
+        outs = {"loss": loss}
+        outs.update(zip(("term", "pixel_unc", "depth", "rgb", "sdf", "z_vals", "depth_unc"), step.rendered()))
+        outs.update({"decoders." + k: v for k, v in dec.state_dict().items()})
+        outs.update(table_sdf=es.params, table_color=ec.params)
+        dumped = {"dir": args.dump_outputs, "after_step": args.warmup + args.steps,
+                  "arrays": dump_outputs(args.dump_outputs, {k: v.detach().cpu().numpy() for k, v in outs.items()})}
 
     # per-step GPU time of the same runner, one HIP event pair per step on the launch stream (median, p10, p90), AFTER the timed
     # region (the K timed steps above are bracketed by nothing but the barrier + synchronize of the contract)
@@ -1051,6 +1099,8 @@ def run_rank(args):
                "launch": (("hipGraph replay of MapWindow.iterate (joint_opt off): pixel draw + gather + sampling in one launch, then MapStep.iterate"
                            if world == 1 else "hipGraph segments of MapWindow.iterate between the collectives (statistics all-reduce, gradient segments)")
                           if (use_graph and fresh and launch_kind["graph"]) else "hipGraph replay of MapStep.iterate" if (use_graph and not fresh) else "eager")}
+        if dumped is not None:
+            rec["dump_outputs"] = dumped
         if kern is not None:
             rec["kernel_ms"] = {k: round(v, 4) for k, v in sorted(kern.items())}
             rec["kernel_ms_note"] = f"median over {max(1, args.probe_steps)} eager one-stream iterations after the timed region"

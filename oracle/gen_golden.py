@@ -6,7 +6,7 @@ sys.modules, in memory), runs its functions on CPU with fixed seeds and stores i
 as small .npz fixtures under tests/golden/.  The reference source never travels; the fixtures are
 data.  Re-run:  python oracle/gen_golden.py      (ALL generators, in file order: g4 / g7 / g8 / g9 take their decoders' initial weights
 from torch's global generator as the generators before them left it; every other fixture, g14 included, is the same when its generator
-runs alone.  tests/test_golden_regen.py regenerates everything into a temporary folder and compares bit for bit.)
+runs alone.  oracle/check_golden.py regenerates everything into a temporary folder and compares bit for bit.)
 
 Fixtures:
   g1_rays      get_camera_rays / get_rays / get_rays_from_uv / get_samples / get_samples_all
@@ -43,7 +43,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-OUT = os.environ.get("US_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")     # (tests/test_golden_regen.py writes to a temp dir)
+OUT = os.environ.get("US_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")     # (oracle/check_golden.py writes to a temp dir)
 REF = "/root/reference"
 
 sys.dont_write_bytecode = True

@@ -92,3 +92,51 @@ def test_request_roofline_of_the_encoder_from_the_committed_curve():
         bench.torch = None
     assert r["lane_loads_per_launch"] == 4 * 3 + (4 * 3 + 4 * 1)
     assert abs(r["achieved"] - r["lane_loads_per_launch"] / 1e-6 / 1e9) < 1e-6 and r["frac"] == pytest.approx(r["ceiling_ms"] / 1e-3)
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files; under the budget every array whole, over it every array of more than 4096
+    elements a seeded sample of its elements in index order -- the same one in every call -- and the small ones whole"""
+    import numpy as np
+    import bench
+    arrays = {"big": np.arange(10000, dtype=np.float64).reshape(100, 100), "small": np.linspace(0, 1, 10)}
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert shapes == {"big": [[100, 100], [100, 100]], "small": [[10], [10]]}
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert b.dtype == np.float32 and np.array_equal(b, a.astype(np.float32))
+    budget = 20000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    files = sorted((tmp_path / "s1").iterdir())
+    assert sum(np.load(f).nbytes for f in files) <= budget
+    big, small = np.load(tmp_path / "s1" / "big.npy"), np.load(tmp_path / "s1" / "small.npy")
+    assert 4000 < big.size < 5000 and np.all(np.diff(big) > 0) and np.array_equal(small, arrays["small"].astype(np.float32))
+    assert np.array_equal(big, np.load(tmp_path / "s2" / "big.npy"))
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_do_not_depend_on_the_set_up_time(tmp_path):
+    """--dump-outputs: two runs with the same arguments but set-up phases of different lengths (--prewarm-s) write the same outputs of
+    the last timed step -- the batch it drew (z_vals) bit for bit, the rest to the rounding of the table gradient's fp32 atomics"""
+    import numpy as np
+    recs = []
+    for run, pre in (("a", "0.05"), ("b", "0.5")):
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "2", "--rays", "512", "--no-extras", "--no-tracking",
+                              "--no-cpu-baseline", "--no-probe", "--prewarm-s", pre, "--dump-outputs", str(tmp_path / run)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        recs.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    assert recs[0]["steps"] == 3 and recs[0]["dump_outputs"]["after_step"] == 5
+    names = sorted(recs[0]["dump_outputs"]["arrays"])
+    assert names == sorted(recs[1]["dump_outputs"]["arrays"])
+    assert {"loss", "depth", "rgb", "z_vals", "table_sdf", "table_color"} <= set(names) and any(n.startswith("decoders.") for n in names)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert sum(x.nbytes for x in a.values()) <= 64 * 2 ** 20 and all(x.dtype == np.float32 for x in a.values())
+    assert np.array_equal(a["z_vals"], b["z_vals"])
+    assert np.isfinite(a["loss"]).all() and np.allclose(a["loss"], b["loss"], rtol=1e-4)
+    for n in ("depth", "rgb"):
+        assert np.allclose(a[n], b[n], rtol=1e-3, atol=1e-4), n
+    for n in names:                              # (an Adam step turns a gradient of rounding size into a full step: a few entries may)
+        assert a[n].shape == b[n].shape and np.mean(~np.isclose(a[n], b[n], rtol=1e-3, atol=1e-4)) < 1e-3, n
